@@ -12,6 +12,8 @@ collective is the all-gather of the rows (lightzero_amd/shard.py), issued asynch
 under the next step's representation tower and that step's search is ordered behind it (--gather-fence).
 
     python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3 --dump-outputs DIR   # + the last timed step's outputs as DIR/*.npy
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full   # + the secondary arms, roofline and CPU / deployed baselines
     python bench.py --gpus 8                       # re-executes itself under torch.distributed.run
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
@@ -589,6 +591,12 @@ def main():
                          "step i + 1 and makes the search wait for it -- the search's chain launch is one workgroup per CU on all 256 CUs, so a "
                          "collective kernel holding even one CU during it costs that launch a second round; 'none' = no ordering")
     ap.add_argument("--check-gather", action="store_true", help="after the timed region: every rank verifies the pooled rows block by block")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also measure everything beside the headline: shader clock, sustained and PCIe-inclusive "
+                         "rates, the other tie-break arm, the roofline pass, the fast-mode / depth-sweep / weight-refresh arms, the policy "
+                         "and collector surfaces and the CPU / deployed baselines (off by default: a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the timed path returned in its last timed step (rank 0) as DIR/<name>.npy")
     args = ap.parse_args()
     if args.cpu_worker:
         _cpu_worker(args.cpu_worker)
@@ -759,7 +767,7 @@ def main():
     sync_all()
     if dist_on:
         dist.barrier()
-    clocks = ClockSampler(device_index).start() if rank == 0 else None
+    clocks = ClockSampler(device_index).start() if (rank == 0 and args.full) else None
     clock_windows = {}
     t0 = time.perf_counter()
     for i in range(args.warmup, total):
@@ -807,11 +815,26 @@ def main():
         ok = ok and torch.equal(pooled[rank * NMAX:rank * NMAX + ENVS], mine)
         gather_check = "ok" if ok else "MISMATCH"
         assert ok, "the pooled rows differ from the ranks' own rows"
-    # ---- secondary arms, rank-local, after the contract's timed region (same process, same roots)
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path receives from its last timed step: the packed env-step rows (header: action, reward, root
+        # value, predicted value, to_play, timestep, entropy, legal count; visit distribution; action mask; newest frame), the root
+        # prior logits, the visit counts and the root values of every root of this rank
+        visits = np.zeros((ENVS, ACTIONS), np.float64)
+        values = np.zeros(ENVS, np.float32)
+        for k, r in enumerate(roots_l):
+            d_k = np.zeros((EPS, ACTIONS), np.int32); c_k = np.zeros(EPS, np.int32); v_k = np.zeros(EPS, np.float32)
+            L.check(lib.lz_roots_get_distributions(r._h, d_k, c_k))
+            L.check(lib.lz_roots_get_values(r._h, v_k))
+            visits[k * EPS:(k + 1) * EPS], values[k * EPS:(k + 1) * EPS] = d_k, v_k
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in (("rows", rows_dev[(total - 1) & 1][:ENVS].cpu().numpy()), ("root_logits", logits), ("visit_counts", visits),
+                        ("root_values", values)):
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), np.ascontiguousarray(a))
+    # ---- secondary arms (--full only), rank-local, after the contract's timed region (same process, same roots)
     # (a) sustained: the contract's K = 20 steps are 0.07 s of GPU work, a burst before the clock settles -- keep stepping for
     #     >= --sustain-s seconds and report that rate too
     sustained = None
-    if args.sustain_s > 0:
+    if args.full and args.sustain_s > 0:
         # the step count comes from the (all-reduced) time of the timed region: identical on every rank, so the row all-gathers match
         n_s = 20 * max(1, int(np.ceil(args.sustain_s / (elapsed / args.steps) / 20)))
         t_s = time.perf_counter()
@@ -823,7 +846,7 @@ def main():
     # (a2) PCIe-inclusive: the same step with the observation batch handed over in (pinned) HOST memory -- lz_initial_inference_host copies the
     #      37.7 MB over PCIe on the engine's stream in front of the tower.  Never `value` (the contract's inputs are resident in HBM).
     host_obs_rate = None
-    if not dist_on and hasattr(lib, "lz_initial_inference_host"):
+    if args.full and not dist_on and hasattr(lib, "lz_initial_inference_host"):
         host_obs[0] = [[o[k * EPS:(k + 1) * EPS].contiguous().pin_memory() for o in obs_pool_cpu] for k in range(NS)]
         n_w = max(2, NOBS)   # every pinned batch once: the first transfer out of a freshly pinned buffer is slower
         for j in range(n_w):
@@ -837,69 +860,69 @@ def main():
         host_obs[0] = None
     if clocks:
         clocks.stop()
-    # (b) the other tie-break arm (the parity tests pin "first": deterministic first arg-max; collection uses the reference's
-    #     stochastic rule): same K steps after W warm-ups, the search graph re-captured for the other rule
     other = "first" if args.tiebreak == "random" else "random"
-    for k, r in enumerate(roots_l):
-        r.set_tiebreak(0 if other == "first" else 1, seed=rank * 16 + k + 1)
-    for i in range(args.warmup):
-        step(i)
-    sync_all()
-    t_o = time.perf_counter()
-    for i in range(args.steps):
-        step(i)
-    sync_all()
-    other_rate = sum(counts) * args.steps / (time.perf_counter() - t_o)   # (rank 0's clock; the ranks run in lock-step through the all-gathers)
-    for k, r in enumerate(roots_l):
-        r.set_tiebreak(0 if args.tiebreak == "first" else 1, seed=rank * 16 + k + 1)
-    # Roofline pass: the timed region replays the search from a captured HIP graph, which cannot carry event
-    # records, so the dominant kernel is timed right after it, same process and inputs, with HIP event pairs recorded
-    # on the engine stream around every k_chain launch of `prof_steps` eagerly launched steps.
-    prof_steps = min(args.steps, 5)
-    L.check(lib.lz_profile_enable(eng, SIMS * prof_steps))
-    for i in range(prof_steps):
-        step(args.warmup + i)
-    drain()
+    other_rate, stamp, prof_steps = None, None, min(args.steps, 5)
     n_launch = ctypes.c_int64(0)
     tot_ms = ctypes.c_double(0.0)
-    L.check(lib.lz_profile_read(eng, ctypes.byref(n_launch), ctypes.byref(tot_ms)))
-    L.check(lib.lz_profile_enable(eng, 0))
+    if args.full:
+        # (b) the other tie-break arm (the parity tests pin "first": deterministic first arg-max; collection uses the reference's
+        #     stochastic rule): same K steps after W warm-ups, the search graph re-captured for the other rule
+        for k, r in enumerate(roots_l):
+            r.set_tiebreak(0 if other == "first" else 1, seed=rank * 16 + k + 1)
+        for i in range(args.warmup):
+            step(i)
+        sync_all()
+        t_o = time.perf_counter()
+        for i in range(args.steps):
+            step(i)
+        sync_all()
+        other_rate = sum(counts) * args.steps / (time.perf_counter() - t_o)   # (rank 0's clock; the ranks run in lock-step through the all-gathers)
+        for k, r in enumerate(roots_l):
+            r.set_tiebreak(0 if args.tiebreak == "first" else 1, seed=rank * 16 + k + 1)
+        # Roofline pass: the timed region replays the search from a captured HIP graph, which cannot carry event
+        # records, so the dominant kernel is timed right after it, same process and inputs, with HIP event pairs recorded
+        # on the engine stream around every k_chain launch of `prof_steps` eagerly launched steps.
+        L.check(lib.lz_profile_enable(eng, SIMS * prof_steps))
+        for i in range(prof_steps):
+            step(args.warmup + i)
+        drain()
+        L.check(lib.lz_profile_read(eng, ctypes.byref(n_launch), ctypes.byref(tot_ms)))
+        L.check(lib.lz_profile_enable(eng, 0))
 
-    # THIS run's clock for the roofline kernel, on the benchmarked (graph-replayed) launch sequence: the first workgroup of every
-    # chain and LSTM launch stores its s_memrealtime start, the last one its end (100 MHz constant-rate counter; lz_roots_enable_stamps;
-    # the search graph is re-captured with the stamp pointers, nothing else changes).  A launch's cost in the stream is the time from
-    # its first workgroup's start to the NEXT launch's first start (execution + drain + dispatch of the successor): that period is
-    # what `frac` divides by; first workgroup's start -> last workgroup's end of the launch itself is reported beside it.
-    stamp = None
-    try:
-        r0 = roots_l[0]
-        L.check(lib.lz_roots_enable_stamps(r0._h, 1))
-        for i in range(2):
-            step(args.warmup + i)
-        per, exe, lper, lexe, sims = [], [], [], [], []
-        st = np.zeros((SIMS, 4), np.uint64)
-        for i in range(max(prof_steps, 5)):
-            step(args.warmup + i)
-            drain()
-            L.check(lib.lz_engine_synchronize(eng))
-            L.check(lib.lz_roots_read_stamps(r0._h, SIMS, st))
-            t = st.astype(np.int64) * 10e-3   # microseconds
-            # simulations 1 .. S-2: the fused launch (tree step + split-head finish + chain) followed by an LSTM launch and another chain
-            per.append(t[1:SIMS - 1, 2] - t[1:SIMS - 1, 0]); exe.append(t[1:SIMS - 1, 1] - t[1:SIMS - 1, 0])
-            lper.append(t[2:SIMS, 0] - t[1:SIMS - 1, 2]); lexe.append(t[1:SIMS - 1, 3] - t[1:SIMS - 1, 2])
-            sims.append(t[SIMS - 1, 3] - t[0, 0])
-        L.check(lib.lz_roots_enable_stamps(r0._h, 0))
-        per, exe, lper, lexe = (np.concatenate(x) for x in (per, exe, lper, lexe))
-        stamp = dict(chain_period_us=float(per.mean()), chain_exec_us=float(exe.mean()), lstm_period_us=float(lper.mean()), lstm_exec_us=float(lexe.mean()),
-                     chain_period_us_min_max=[float(per.min()), float(per.max())], launches=int(per.size),
-                     search_us=float(np.mean(sims)), per_simulation_us=float((per.mean() + lper.mean())))
-    except Exception as e:   # (an older library without the stamp entry points: the HIP-event pass below still gives a clock)
-        stamp = dict(error=repr(e))
+        # THIS run's clock for the roofline kernel, on the benchmarked (graph-replayed) launch sequence: the first workgroup of every
+        # chain and LSTM launch stores its s_memrealtime start, the last one its end (100 MHz constant-rate counter; lz_roots_enable_stamps;
+        # the search graph is re-captured with the stamp pointers, nothing else changes).  A launch's cost in the stream is the time from
+        # its first workgroup's start to the NEXT launch's first start (execution + drain + dispatch of the successor): that period is
+        # what `frac` divides by; first workgroup's start -> last workgroup's end of the launch itself is reported beside it.
+        try:
+            r0 = roots_l[0]
+            L.check(lib.lz_roots_enable_stamps(r0._h, 1))
+            for i in range(2):
+                step(args.warmup + i)
+            per, exe, lper, lexe, sims = [], [], [], [], []
+            st = np.zeros((SIMS, 4), np.uint64)
+            for i in range(max(prof_steps, 5)):
+                step(args.warmup + i)
+                drain()
+                L.check(lib.lz_engine_synchronize(eng))
+                L.check(lib.lz_roots_read_stamps(r0._h, SIMS, st))
+                t = st.astype(np.int64) * 10e-3   # microseconds
+                # simulations 1 .. S-2: the fused launch (tree step + split-head finish + chain) followed by an LSTM launch and another chain
+                per.append(t[1:SIMS - 1, 2] - t[1:SIMS - 1, 0]); exe.append(t[1:SIMS - 1, 1] - t[1:SIMS - 1, 0])
+                lper.append(t[2:SIMS, 0] - t[1:SIMS - 1, 2]); lexe.append(t[1:SIMS - 1, 3] - t[1:SIMS - 1, 2])
+                sims.append(t[SIMS - 1, 3] - t[0, 0])
+            L.check(lib.lz_roots_enable_stamps(r0._h, 0))
+            per, exe, lper, lexe = (np.concatenate(x) for x in (per, exe, lper, lexe))
+            stamp = dict(chain_period_us=float(per.mean()), chain_exec_us=float(exe.mean()), lstm_period_us=float(lper.mean()), lstm_exec_us=float(lexe.mean()),
+                         chain_period_us_min_max=[float(per.min()), float(per.max())], launches=int(per.size),
+                         search_us=float(np.mean(sims)), per_simulation_us=float((per.mean() + lper.mean())))
+        except Exception as e:   # (an older library without the stamp entry points: the HIP-event pass below still gives a clock)
+            stamp = dict(error=repr(e))
 
     # The committed rocprofv3 summary (profiles/r04_manifest.json) is used only when it was measured on the kernel sources this run is
     # built from (digest of csrc/): then the roofline divides by the profiler's average launch duration and carries the PMC traffic;
     # otherwise by this run's own HIP-event pairs (which include the gaps of eager launches) with traffic null.
-    man = _profile_manifest()
+    man = _profile_manifest() if args.full else None
     traffic = man["k_chain"]["hbm_bytes_per_launch"] if man else None
     if rank == 0:
         value = sum(counts) * args.steps / elapsed
@@ -923,7 +946,7 @@ def main():
             "config": {"workload": "BASELINE.json configs[1]: Atari Pong EfficientZero, obs 4x96x96, 50 sims, "
                                    "256 envs per GPU, A=6, support 601, LSTM 512; synthetic obs, seed-0 random-init weights; dtype f32 = binary32 operands and "
                                    "accumulators, the 3x3 convolutions' products evaluated as six exact bf16 x bf16 plane products per k-step (config.arithmetic)",
-                       "envs_per_gpu": ENVS, "envs_per_rank": counts, "total_envs": sum(counts), "num_simulations": SIMS,
+                       "full": bool(args.full), "envs_per_gpu": ENVS, "envs_per_rank": counts, "total_envs": sum(counts), "num_simulations": SIMS,
                        "weight_refresh_every": args.refresh_every, "gather_check": gather_check, "mcts_sims_per_s": value * SIMS,
                        "tiebreak": args.tiebreak, "tiebreak_%s_env_steps_per_s" % other: other_rate,
                        "root_noise": "drawn on the device inside every step (lz_roots_prepare_from_inference_dirichlet)" if args.noise == "device"
@@ -974,6 +997,7 @@ def main():
             out["config"]["mode"] = ("fast mode (EfficientZeroModel(fast_mode=True), lz_model_cfg.precision = 1): bf16 MFMA with fp32 accumulation for the recurrent "
                                      "chain's 3x3 convolutions (k_chain_b) and the LSTM gate product (k_lstm_b); representation tower, normalisation, cell, heads "
                                      "and tree in fp32; statistical parity only (tests/test_fast_mode_gpu.py) -- NOT the parity-mode headline")
+        if args.fast and args.full:
             rf = out["roofline"]
             rf["kernel"] = "k_chain_b (the same launch as k_chain_s3 with ONE bf16 product per k-step: the 3x3 convolutions in the direct form on v_mfma_f32_16x16x32_bf16)"
             rf["peak"] = PEAK_BF16_MATRIX_TFLOPS
@@ -989,7 +1013,9 @@ def main():
                              search_depth_note="depth of the node each of the 50 simulations expanded (== its search-path length), all roots of "
                                                "the last timed step; observations: %d distinct batches cycled by step" % NOBS,
                              obs_batches=NOBS)
-        if world == 1 and not args.fast and NS == 1:
+        if not args.full:   # the roofline needs the passes after the timed region
+            out["roofline"] = None
+        if args.full and world == 1 and not args.fast and NS == 1:
             try:
                 out["fast_mode"] = fast_mode_arm(weights, obs_pool, args.steps, args.warmup)
             except Exception as e:   # a secondary arm never takes the measured line down with it
@@ -1000,7 +1026,7 @@ def main():
                 out["config"].update(weight_refresh(models[0], weights, roots_l[0], step, args.warmup))
             except Exception as e:
                 out["config"]["weight_refresh_ms"] = repr(e)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 out["config"]["policy_surface_env_steps_per_s"] = policy_surface(models[0], obs)
             except Exception as e:

@@ -15,7 +15,7 @@ pytestmark = pytest.mark.gpu
 
 def _run(*extra, gpus="2", env_extra=None):
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", **(env_extra or {}))
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", gpus, "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--sustain-s", "0",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", gpus, "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline", "--sustain-s", "0",
                         "--check-gather"] + list(extra), cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

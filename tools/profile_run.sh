@@ -10,12 +10,12 @@ rm -rf gpurun_out/parity
 timeout 900 python -m pytest tests -m gpu -q -p no:cacheprovider > $R/pytest_gpu.log 2>&1
 tail -3 $R/pytest_gpu.log
 mkdir -p $R/parity && cp gpurun_out/parity/*.json $R/parity/ 2>/dev/null
-timeout 900 python bench.py > $R/bench_n1.json 2> $R/bench_n1.err
+timeout 900 python bench.py --full > $R/bench_n1.json 2> $R/bench_n1.err
 cd /tmp && export TMPDIR=/tmp
-timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $ROOT/$R/stats -- python $ROOT/bench.py --steps 15 --warmup 2 --no-cpu-baseline --sustain-s 0 > /dev/null 2>&1
-timeout 300 rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAVE_CYCLES SQ_LDS_BANK_CONFLICT SQ_ACTIVE_INST_ANY --output-format csv -d $ROOT/$R/pmc_sq -- python $ROOT/bench.py --steps 1 --warmup 1 --no-cpu-baseline --sustain-s 0 > /dev/null 2>&1
-timeout 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $ROOT/$R/pmc_fetch -- python $ROOT/bench.py --steps 1 --warmup 1 --no-cpu-baseline --sustain-s 0 > /dev/null 2>&1
-timeout 300 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $ROOT/$R/pmc_write -- python $ROOT/bench.py --steps 1 --warmup 1 --no-cpu-baseline --sustain-s 0 > /dev/null 2>&1
+timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $ROOT/$R/stats -- python $ROOT/bench.py --full --steps 15 --warmup 2 --no-cpu-baseline --sustain-s 0 > /dev/null 2>&1
+timeout 300 rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAVE_CYCLES SQ_LDS_BANK_CONFLICT SQ_ACTIVE_INST_ANY --output-format csv -d $ROOT/$R/pmc_sq -- python $ROOT/bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --sustain-s 0 > /dev/null 2>&1
+timeout 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $ROOT/$R/pmc_fetch -- python $ROOT/bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --sustain-s 0 > /dev/null 2>&1
+timeout 300 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $ROOT/$R/pmc_write -- python $ROOT/bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --sustain-s 0 > /dev/null 2>&1
 cd $ROOT
 # the per-dispatch traces are large: keep the summaries
 find $R -name "*kernel_trace.csv" -delete

@@ -61,7 +61,7 @@ def main():
     fused = short(fused)
     f, w = mean(fused, "FETCH_SIZE"), mean(fused, "WRITE_SIZE")
     out = {"_how": "rocprofv3 --kernel-trace --pmc FETCH_SIZE and rocprofv3 --kernel-trace --pmc WRITE_SIZE (two separate passes) -- "
-                   "python bench.py --steps 1 --warmup 1 --no-cpu-baseline, MI355X; per-dispatch means in KB as reported "
+                   "python bench.py --full --steps 1 --warmup 1 --no-cpu-baseline, MI355X; per-dispatch means in KB as reported "
                    "(tools/refresh_profiles.py). gfx950 correction (MI355X_MICROARCH.md, HBM): FETCH_SIZE counts 64 B per 128-B "
                    "request of a wide coalesced read, so read bytes = 2 x FETCH_SIZE; WRITE_SIZE taken as reported (uncalibrated).",
            "k_chain": {"fetch_size_kb": f, "write_size_kb": w, "hbm_bytes_per_launch": int(round((2 * f + w) * 1024)),
@@ -107,7 +107,7 @@ def main():
     busy = mean(fused, "SQ_VALU_MFMA_BUSY_CYCLES")
     d_us = d_chain
     hdr = ["# rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAVE_CYCLES SQ_LDS_BANK_CONFLICT SQ_ACTIVE_INST_ANY",
-           "#   + separate passes --pmc FETCH_SIZE / --pmc WRITE_SIZE   -- python bench.py --steps 1 --warmup 1 --no-cpu-baseline   (MI355X)",
+           "#   + separate passes --pmc FETCH_SIZE / --pmc WRITE_SIZE   -- python bench.py --full --steps 1 --warmup 1 --no-cpu-baseline   (MI355X)",
            "# per-dispatch means.  Counters are summed over the 8 XCDs / 1024 SIMDs; SQ_WAVE_CYCLES / SQ_ACTIVE_INST_ANY count quad-cycles;",
            "# SQ_VALU_MFMA_BUSY_CYCLES counts cycles per SIMD (32 per v_mfma_f32_16x16x4_f32, 16 per v_mfma_f32_16x16x32_bf16);",
            "# k_chain_s3 runs 324 16x16x32 bf16 MFMAs per SIMD and layer (9 taps x 2 K halves x 6 plane products x 3 pixel tiles): 5,184 busy cycles;",

@@ -1,8 +1,9 @@
 #!/bin/bash
 # per-dispatch durations of the representation tower's kernels (one env-step), from a rocprofv3 kernel trace
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 R=$GRAFT_REPO_ROOT/gpurun_out/tower_trace; mkdir -p $R
 cd /tmp && export TMPDIR=/tmp
-timeout 300 rocprofv3 --kernel-trace --output-format csv -d $R -- python $GRAFT_REPO_ROOT/bench.py --steps 2 --warmup 1 --no-cpu-baseline --sustain-s 0 > /dev/null 2>&1
+timeout 300 rocprofv3 --kernel-trace --output-format csv -d $R -- python $ROOT/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --sustain-s 0 > /dev/null 2>&1
 cd $GRAFT_REPO_ROOT
 python - <<'PY'
 import csv, glob, os
